@@ -19,13 +19,17 @@ encoded to the .xsi blocks region and decoded back to packed bits.  Workloads (B
 torch.distributed.run, before this process touches the GPU; under a launcher it is rank RANK of WORLD_SIZE.
 
 The default command (no flags: configs[2] on one GPU) counts the rows' ALT alleles on the device INSIDE the timed
-step (xsi_hip_encode_packed; --producer-counts is the opt-in for callers whose producer has the counts) and then
-runs configs[1], the configs[3] shard of one of 8 GPUs and configs[4] in the same process, attached to the same JSON
-line as `other_configs` (each with its own ms_per_step, roofline and parity flags; --no-other-configs skips them).
+step (xsi_hip_encode_packed; --producer-counts is the opt-in for callers whose producer has the counts).  A plain run
+sets up, warms up, times --steps steps, checks that the last step's round trip equals its input and prints the line.
+--full adds everything else: the CPU-oracle baseline and the byte comparison of the first blocks with it; configs[1],
+the configs[3] shard of one of 8 GPUs and configs[4] in the same process, attached to the same JSON line as
+`other_configs` (each with its own ms_per_step, roofline and parity flags; --no-other-configs skips them); at N > 1
+the north_star job; the row count and the gather timed on their own.
+--dump-outputs DIR writes what the last timed step computed (samples of the larger arrays, see dump_outputs).
 
 No data-path collective: blocks are independent.  The path's one exchange step, the gather of the
 compressed block streams to the writer rank over RCCL, runs inside the timed region (overlapped with the
-decode) and is also timed on its own after it (`gather_ms`).  Prints ONE JSON line on rank 0.
+decode) and, with --full, is also timed on its own after it (`gather_ms`).  Prints ONE JSON line on rank 0.
 """
 import argparse
 import ctypes
@@ -64,6 +68,29 @@ LDS_CYCLES_PER_CHUNK_LINE = {"k_chain_rank_enc": 9.7, "k_chain_decode_rank_wg": 
 
 
 HBM_BYTES = 288 * 10**9  # MI355X, per GPU
+
+# --dump-outputs: outputs larger than this many values are written as a sample at fixed positions (a seeded draw that
+# depends only on the output's size), so that two builds run with the same arguments can be compared value for value
+DUMP_SEED = 7919
+DUMP_VALUES = 4 << 20  # per sampled array: 16 MB of float32
+
+
+def sample_positions(n, k, salt):
+    """Sorted distinct positions of [0, n): all of them when n <= k, else at most k drawn with a fixed seed."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng([DUMP_SEED, salt]).integers(0, n, k))
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array (float32 or float64), at most 64 MB in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > (64 << 20):
+        raise SystemExit("--dump-outputs: %d bytes of outputs is over the 64 MB limit" % total)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def job_shape(args, world, rank):
@@ -166,7 +193,7 @@ def dry_launch_rank(args, real_stdout):
                "held_bytes_per_rank": [int(t[4]) for t in got], "fits_per_rank": [bool(t[5]) for t in got],
                "hbm_bytes": HBM_BYTES, "memory_plan_rank0": plan,
                "also_runs": ("--config 3 strong-scaled over the same ranks, attached as other_configs"
-                             if (world > 1 and args.config == 2 and not args.no_other_configs) else None)}
+                             if (world > 1 and args.config == 2 and args.full and not args.no_other_configs) else None)}
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     tdist.destroy_process_group()
     return 0
@@ -270,9 +297,15 @@ def run_config4(args, real_stdout, emit=True):
     get = L.xsi_accessor_get_genotypes
     u64 = ctypes.c_uint64
 
-    def one_pass(check_every):
+    # --dump-outputs: the rows the last timed step returns for a fixed sample of its queries, as float64 (exact for int32,
+    # so the end-of-vector and missing values stay apart)
+    keep_k = sample_positions(len(all_lines), max(1, 3 * DUMP_VALUES // (2 * N)), 3) if args.dump_outputs else np.zeros(0, np.int64)
+    keep_slot = {int(k): i for i, k in enumerate(keep_k)}
+    kept = np.zeros((len(keep_k), N), dtype=np.float64)
+
+    def one_pass(check_every, keep=False):
         """All queries of a step through xsi_accessor_get_genotypes; every check_every-th row is compared with the
-        source row (the comparison's time is taken out)."""
+        source row (the comparison's time is taken out); keep: the rows of the queries in keep_slot go to `kept`."""
         ok = True
         t_chk = 0.0
         t = time.perf_counter()
@@ -280,6 +313,8 @@ def run_config4(args, real_stdout, emit=True):
             r = get(a, int(all_na[k]), int(all_bm[k]), ctypes.byref(pbuf), ctypes.byref(nout))
             if r != N:
                 raise SystemExit("get_genotypes failed: %s" % L.xsi_hip_last_error())
+            if keep and k in keep_slot:
+                kept[keep_slot[k]] = buf
             if check_every and k % check_every == 0:
                 tc = time.perf_counter()
                 ok = ok and bool(np.array_equal(buf, rows[int(all_lines[k])].cpu().numpy()))
@@ -302,123 +337,128 @@ def run_config4(args, real_stdout, emit=True):
     fence()
     t0 = time.perf_counter()
     ok_warm = True
-    for _ in range(steps):
-        _, okp = one_pass(0)
+    for i in range(steps):
+        _, okp = one_pass(0, keep=(i == steps - 1))
         ok_warm = ok_warm and okp
     fence()
     dt = time.perf_counter() - t0
-    _, ok_chk = one_pass(499)  # the same queries again, checked against the source rows (not timed)
-    # ---- the random queries again through ONE call per batch (xsi_accessor_get_genotypes_batch): the kernels store the
-    # rows of a batch into a page-locked array of args.batch rows; one launch per block touched, one completion ----
-    binding.check(L.xsi_accessor_unregister_array(a))
-    nb_rows = max(1, min(args.batch, len(q_lines)))
-    bat = torch.empty((nb_rows, N), dtype=torch.int32, pin_memory=True)
-    bat_np = bat.numpy()
-    binding.check(L.xsi_accessor_register_array(a, bat_np.ctypes.data, bat_np.size))
-    q_bm = np.ascontiguousarray(all_bm[:len(q_lines)], dtype=np.uint64)
-    q_na = np.ascontiguousarray(all_na[:len(q_lines)], dtype=np.uint32)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rows_sample": kept, "rows_sample_queries": keep_k.astype(np.float64)})
+    ok_chk = ok_batched = True
+    seq_new = seq_old = None
+    if args.full:  # the checked pass, the batched calls, cold single queries and cold sequential scans
+        _, ok_chk = one_pass(499)  # the same queries again, checked against the source rows (not timed)
+        # ---- the random queries again through ONE call per batch (xsi_accessor_get_genotypes_batch): the kernels store the
+        # rows of a batch into a page-locked array of args.batch rows; one launch per block touched, one completion ----
+        binding.check(L.xsi_accessor_unregister_array(a))
+        nb_rows = max(1, min(args.batch, len(q_lines)))
+        bat = torch.empty((nb_rows, N), dtype=torch.int32, pin_memory=True)
+        bat_np = bat.numpy()
+        binding.check(L.xsi_accessor_register_array(a, bat_np.ctypes.data, bat_np.size))
+        q_bm = np.ascontiguousarray(all_bm[:len(q_lines)], dtype=np.uint64)
+        q_na = np.ascontiguousarray(all_na[:len(q_lines)], dtype=np.uint32)
 
-    def batched_pass(check):
-        ok = True
-        t_chk = 0.0
-        t = time.perf_counter()
-        for b0 in range(0, len(q_lines), nb_rows):
-            m = min(nb_rows, len(q_lines) - b0)
-            r = L.xsi_accessor_get_genotypes_batch(a, m, q_na[b0:].ctypes.data, q_bm[b0:].ctypes.data, bat_np.ctypes.data, N, None)
-            if r != m * N:
-                raise SystemExit("get_genotypes_batch failed: %s" % L.xsi_hip_last_error())
-            if check:
-                tc = time.perf_counter()
-                for k in range(0, m, 37):
-                    ok = ok and bool(np.array_equal(bat_np[k], rows[int(q_lines[b0 + k])].cpu().numpy()))
-                t_chk += time.perf_counter() - tc
-        return time.perf_counter() - t - t_chk, ok
+        def batched_pass(check):
+            ok = True
+            t_chk = 0.0
+            t = time.perf_counter()
+            for b0 in range(0, len(q_lines), nb_rows):
+                m = min(nb_rows, len(q_lines) - b0)
+                r = L.xsi_accessor_get_genotypes_batch(a, m, q_na[b0:].ctypes.data, q_bm[b0:].ctypes.data, bat_np.ctypes.data, N, None)
+                if r != m * N:
+                    raise SystemExit("get_genotypes_batch failed: %s" % L.xsi_hip_last_error())
+                if check:
+                    tc = time.perf_counter()
+                    for k in range(0, m, 37):
+                        ok = ok and bool(np.array_equal(bat_np[k], rows[int(q_lines[b0 + k])].cpu().numpy()))
+                    t_chk += time.perf_counter() - tc
+            return time.perf_counter() - t - t_chk, ok
 
-    # ---- cold isolated queries: the block is not in HBM, ONE line at binary-line offset o is asked for.  The first
-    # touch runs the chain over the WAH lines in front of o only (what the reference's seek replays on the host,
-    # accessor_internals_new.hpp:154-196), so its cost scales with o; full_block_ms is the same query with
-    # XSI_ACCESSOR_FULL_DECODE=1 (the whole block decoded on first touch, as before round 4) ----
-    cold_iso = []
-    binding.check(L.xsi_accessor_unregister_array(a))
-    binding.check(L.xsi_accessor_register_array(a, buf.ctypes.data, buf.size))
-    budget_before = int(cby.value) * 4 + (8 << 30)
-    line_of_block0 = np.arange(min(bl, S))
-    for frac in (0.3, 1.0 / 128, 1.0 / 16, 0.25, 0.5, 0.97):  # the first one warms the path up and is dropped
-        li = int(line_of_block0[int(frac * (len(line_of_block0) - 1))])
-        rec = {"line": li, "bm_offset": int(bm[li] & 0x7FFF)}
-        for mode in ("prefix", "full"):
+        # ---- cold isolated queries: the block is not in HBM, ONE line at binary-line offset o is asked for.  The first
+        # touch runs the chain over the WAH lines in front of o only (what the reference's seek replays on the host,
+        # accessor_internals_new.hpp:154-196), so its cost scales with o; full_block_ms is the same query with
+        # XSI_ACCESSOR_FULL_DECODE=1 (the whole block decoded on first touch, as before round 4) ----
+        cold_iso = []
+        binding.check(L.xsi_accessor_unregister_array(a))
+        binding.check(L.xsi_accessor_register_array(a, buf.ctypes.data, buf.size))
+        budget_before = int(cby.value) * 4 + (8 << 30)
+        line_of_block0 = np.arange(min(bl, S))
+        for frac in (0.3, 1.0 / 128, 1.0 / 16, 0.25, 0.5, 0.97):  # the first one warms the path up and is dropped
+            li = int(line_of_block0[int(frac * (len(line_of_block0) - 1))])
+            rec = {"line": li, "bm_offset": int(bm[li] & 0x7FFF)}
+            for mode in ("prefix", "full"):
+                had_switch = os.environ.get("XSI_ENABLE_TUNING_ENV")
+                if mode == "full":  # (the library ignores its tuning variables unless the process opts in)
+                    os.environ["XSI_ENABLE_TUNING_ENV"] = "1"
+                    os.environ["XSI_ACCESSOR_FULL_DECODE"] = "1"
+                binding.check(L.xsi_accessor_set_cache_bytes(a, 0))       # evict everything
+                binding.check(L.xsi_accessor_set_cache_bytes(a, budget_before))
+                torch.cuda.synchronize()
+                tq = time.perf_counter()
+                r = get(a, int(nal[li]), int(bm[li]), ctypes.byref(pbuf), ctypes.byref(nout))
+                rec[mode + "_ms"] = (time.perf_counter() - tq) * 1e3
+                os.environ.pop("XSI_ACCESSOR_FULL_DECODE", None)
+                if had_switch is None:
+                    os.environ.pop("XSI_ENABLE_TUNING_ENV", None)
+                if r != N or not np.array_equal(buf, rows[li].cpu().numpy()):
+                    raise SystemExit("cold query at line %d (%s) failed: %s" % (li, mode, L.xsi_hip_last_error()))
+            cold_iso.append(rec)
+        cold_iso = cold_iso[1:]
+
+        # ---- cold sequential scan (the reference's own benchmark loads every line in order,
+        # loading_time/gt_loader_new.hpp:112-172): nothing in HBM, then every line of the first blocks in file order, one
+        # get_genotypes call per line.  "stalls" = calls that took more than a millisecond (first touches and continuations of a
+        # prefix decode).  Measured twice: with the accessor's sequential policy (one continuation per prefix-decoded block,
+        # whole-block first touches, block b + 1 decoded by a second thread while b is served) and with
+        # XSI_ACCESSOR_NO_READAHEAD=1, which is the accessor of rounds 4 - 5.
+        def seq_scan(readahead):
             had_switch = os.environ.get("XSI_ENABLE_TUNING_ENV")
-            if mode == "full":  # (the library ignores its tuning variables unless the process opts in)
+            if not readahead:
                 os.environ["XSI_ENABLE_TUNING_ENV"] = "1"
-                os.environ["XSI_ACCESSOR_FULL_DECODE"] = "1"
+                os.environ["XSI_ACCESSOR_NO_READAHEAD"] = "1"
             binding.check(L.xsi_accessor_set_cache_bytes(a, 0))       # evict everything
             binding.check(L.xsi_accessor_set_cache_bytes(a, budget_before))
             torch.cuda.synchronize()
-            tq = time.perf_counter()
-            r = get(a, int(nal[li]), int(bm[li]), ctypes.byref(pbuf), ctypes.byref(nout))
-            rec[mode + "_ms"] = (time.perf_counter() - tq) * 1e3
-            os.environ.pop("XSI_ACCESSOR_FULL_DECODE", None)
+            n_scan = min(4, n_blocks) * bl
+            lat = np.empty(n_scan)
+            ok = True
+            ra0, rh0 = u64(0), u64(0)
+            binding.check(L.xsi_accessor_readahead_stats(a, ctypes.byref(ra0), ctypes.byref(rh0)))
+            t_scan = 0.0
+            for li in range(n_scan):
+                tq = time.perf_counter()
+                r = get(a, int(nal[li]), int(bm[li]), ctypes.byref(pbuf), ctypes.byref(nout))
+                lat[li] = time.perf_counter() - tq
+                t_scan += lat[li]
+                if r != N:
+                    raise SystemExit("sequential scan failed at line %d: %s" % (li, L.xsi_hip_last_error()))
+                if li % 509 == 0:
+                    ok = ok and bool(np.array_equal(buf, rows[li].cpu().numpy()))
+            os.environ.pop("XSI_ACCESSOR_NO_READAHEAD", None)
             if had_switch is None:
                 os.environ.pop("XSI_ENABLE_TUNING_ENV", None)
-            if r != N or not np.array_equal(buf, rows[li].cpu().numpy()):
-                raise SystemExit("cold query at line %d (%s) failed: %s" % (li, mode, L.xsi_hip_last_error()))
-        cold_iso.append(rec)
-    cold_iso = cold_iso[1:]
+            ra1, rh1 = u64(0), u64(0)
+            binding.check(L.xsi_accessor_readahead_stats(a, ctypes.byref(ra1), ctypes.byref(rh1)))
+            return {"lines": n_scan, "seconds": t_scan, "lines_per_s": n_scan / t_scan, "cells_per_s": float(N) * n_scan / t_scan,
+                    "stalls_over_1ms": int((lat > 1e-3).sum()), "stall_ms_total": float(lat[lat > 1e-3].sum() * 1e3),
+                    "max_call_ms": float(lat.max() * 1e3), "median_call_us": float(np.median(lat) * 1e6),
+                    "stall_calls": [[int(i), round(float(lat[i]) * 1e3, 2)] for i in np.nonzero(lat > 1e-3)[0][:24]],
+                    "readaheads_started": int(ra1.value - ra0.value), "first_touches_served_by_readahead": int(rh1.value - rh0.value),
+                    "rows_match_source": ok}
 
-    # ---- cold sequential scan (the reference's own benchmark loads every line in order,
-    # loading_time/gt_loader_new.hpp:112-172): nothing in HBM, then every line of the first blocks in file order, one
-    # get_genotypes call per line.  "stalls" = calls that took more than a millisecond (first touches and continuations of a
-    # prefix decode).  Measured twice: with the accessor's sequential policy (one continuation per prefix-decoded block,
-    # whole-block first touches, block b + 1 decoded by a second thread while b is served) and with
-    # XSI_ACCESSOR_NO_READAHEAD=1, which is the accessor of rounds 4 - 5.
-    def seq_scan(readahead):
-        had_switch = os.environ.get("XSI_ENABLE_TUNING_ENV")
-        if not readahead:
-            os.environ["XSI_ENABLE_TUNING_ENV"] = "1"
-            os.environ["XSI_ACCESSOR_NO_READAHEAD"] = "1"
-        binding.check(L.xsi_accessor_set_cache_bytes(a, 0))       # evict everything
-        binding.check(L.xsi_accessor_set_cache_bytes(a, budget_before))
-        torch.cuda.synchronize()
-        n_scan = min(4, n_blocks) * bl
-        lat = np.empty(n_scan)
-        ok = True
-        ra0, rh0 = u64(0), u64(0)
-        binding.check(L.xsi_accessor_readahead_stats(a, ctypes.byref(ra0), ctypes.byref(rh0)))
-        t_scan = 0.0
-        for li in range(n_scan):
-            tq = time.perf_counter()
-            r = get(a, int(nal[li]), int(bm[li]), ctypes.byref(pbuf), ctypes.byref(nout))
-            lat[li] = time.perf_counter() - tq
-            t_scan += lat[li]
-            if r != N:
-                raise SystemExit("sequential scan failed at line %d: %s" % (li, L.xsi_hip_last_error()))
-            if li % 509 == 0:
-                ok = ok and bool(np.array_equal(buf, rows[li].cpu().numpy()))
-        os.environ.pop("XSI_ACCESSOR_NO_READAHEAD", None)
-        if had_switch is None:
-            os.environ.pop("XSI_ENABLE_TUNING_ENV", None)
-        ra1, rh1 = u64(0), u64(0)
-        binding.check(L.xsi_accessor_readahead_stats(a, ctypes.byref(ra1), ctypes.byref(rh1)))
-        return {"lines": n_scan, "seconds": t_scan, "lines_per_s": n_scan / t_scan, "cells_per_s": float(N) * n_scan / t_scan,
-                "stalls_over_1ms": int((lat > 1e-3).sum()), "stall_ms_total": float(lat[lat > 1e-3].sum() * 1e3),
-                "max_call_ms": float(lat.max() * 1e3), "median_call_us": float(np.median(lat) * 1e6),
-                "stall_calls": [[int(i), round(float(lat[i]) * 1e3, 2)] for i in np.nonzero(lat > 1e-3)[0][:24]],
-                "readaheads_started": int(ra1.value - ra0.value), "first_touches_served_by_readahead": int(rh1.value - rh0.value),
-                "rows_match_source": ok}
-
-    seq_scan(True)  # (warms the second context up: its workspace is allocated on first use)
-    seq_new = seq_scan(True)
-    seq_old = seq_scan(False)
-    binding.check(L.xsi_accessor_unregister_array(a))
-    binding.check(L.xsi_accessor_register_array(a, bat_np.ctypes.data, bat_np.size))
-    batched_pass(False)
-    fence()
-    t_b0 = time.perf_counter()
-    for _ in range(steps):
+        seq_scan(True)  # (warms the second context up: its workspace is allocated on first use)
+        seq_new = seq_scan(True)
+        seq_old = seq_scan(False)
+        binding.check(L.xsi_accessor_unregister_array(a))
+        binding.check(L.xsi_accessor_register_array(a, bat_np.ctypes.data, bat_np.size))
         batched_pass(False)
-    fence()
-    dt_batched = (time.perf_counter() - t_b0) / steps
-    _, ok_batched = batched_pass(True)
+        fence()
+        t_b0 = time.perf_counter()
+        for _ in range(steps):
+            batched_pass(False)
+        fence()
+        dt_batched = (time.perf_counter() - t_b0) / steps
+        _, ok_batched = batched_pass(True)
     binding.check(L.xsi_accessor_cache_stats(a, ctypes.byref(cb), ctypes.byref(cby), ctypes.byref(hits), ctypes.byref(misses)))
     timed_misses = int(misses.value) - cold_misses
     if distributed:
@@ -458,22 +498,24 @@ def run_config4(args, real_stdout, emit=True):
                           # touches cost (decode of all the block's lines to planes in HBM, cache allocation)
                           "ms_per_block_decode": 1e3 * max(t_cold - dt / steps, 0.0) / max(cold_misses, 1)},
             "build": {"synth_s": t_synth, "encode_gt_s": t_encode, "encode_cells_per_s": float(N) * S / t_encode},
-            "batched": {"what": "the %d random queries of the step through xsi_accessor_get_genotypes_batch, %d per call, rows stored by "
-                                "the compose kernels into a page-locked array" % (len(q_lines), nb_rows),
-                        "us_per_query": dt_batched / max(len(q_lines), 1) * 1e6,
-                        "value": float(N) * len(q_lines) / dt_batched, "unit": "GT cells/s",
-                        "host_GBps": 4.0 * float(N) * len(q_lines) / dt_batched / 1e9,
-                        "rows_match_source": bool(ok_batched)},
-            "cold_isolated_queries": {"what": "one line asked of a block that is not in HBM, at rising offsets into the block: "
-                                              "prefix_ms = first touch decodes the lines in front of it only, full_ms = the whole block",
-                                      "block_lines": int(min(bl, S)), "queries": cold_iso},
-            "cold_sequential_scan": dict(seq_new, what="every line of %d cold blocks in file order, one xsi_accessor_get_genotypes "
-                                                       "call per line (int32 rows into a registered page-locked array)" % min(4, n_blocks),
-                                         without_sequential_policy=seq_old,
-                                         speedup=seq_new["lines_per_s"] / seq_old["lines_per_s"]),
-            "rows_match_source": bool(ok_cold and ok_warm and ok_chk and ok_batched and seq_new["rows_match_source"] and seq_old["rows_match_source"]),
         }
-        if not args.no_cpu_baseline:
+        if args.full:
+            out["batched"] = {"what": "the %d random queries of the step through xsi_accessor_get_genotypes_batch, %d per call, rows "
+                                      "stored by the compose kernels into a page-locked array" % (len(q_lines), nb_rows),
+                              "us_per_query": dt_batched / max(len(q_lines), 1) * 1e6,
+                              "value": float(N) * len(q_lines) / dt_batched, "unit": "GT cells/s",
+                              "host_GBps": 4.0 * float(N) * len(q_lines) / dt_batched / 1e9,
+                              "rows_match_source": bool(ok_batched)}
+            out["cold_isolated_queries"] = {"what": "one line asked of a block that is not in HBM, at rising offsets into the block: "
+                                                    "prefix_ms = first touch decodes the lines in front of it only, full_ms = the whole block",
+                                            "block_lines": int(min(bl, S)), "queries": cold_iso}
+            out["cold_sequential_scan"] = dict(seq_new, what="every line of %d cold blocks in file order, one xsi_accessor_get_genotypes "
+                                                             "call per line (int32 rows into a registered page-locked array)" % min(4, n_blocks),
+                                               without_sequential_policy=seq_old,
+                                               speedup=seq_new["lines_per_s"] / seq_old["lines_per_s"])
+        out["rows_match_source"] = bool(ok_cold and ok_warm and ok_chk and ok_batched
+                                        and (seq_new is None or (seq_new["rows_match_source"] and seq_old["rows_match_source"])))
+        if args.full and not args.no_cpu_baseline:
             from oracle import oracle
             rd = oracle.Reader(image)
             ks = list(range(min(args.cpu_queries, len(q_lines))))
@@ -550,7 +592,16 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="config 4: lines per xsi_accessor_get_genotypes_batch call (64: 44 GB/s of rows into host memory, 256: 50, 1024: 52)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher check without a GPU: the ranks only form a gloo group and report in (CPU test)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU-oracle baselines, other_configs, the north_star job at N > 1, "
+                         "the row count and the gather timed on their own, config 4's cold / sequential / batched passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # No launcher around us: start the N ranks ourselves, as CHILD processes of torch.distributed.run, before
         # anything in this process has touched HIP (a process that has initialised the GPU must never exec).
@@ -566,11 +617,12 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     custom = args.haps is not None or args.sites is not None
-    if rank == 0 and world == 1 and ok and args.config == 2 and not custom and not args.no_other_configs and not args.force_dist:
+    full_default = args.full and args.config == 2 and not custom and not args.no_other_configs
+    if rank == 0 and world == 1 and ok and full_default and not args.force_dist:
         # The other single-GPU configurations of BASELINE.json in the same process, attached to the same line, so
         # that they are timed by whoever runs this command and not only by the builder (VERDICT r3 #1b).
         out["other_configs"] = run_other_configs(args, t_start)
-    if (world > 1 or args.force_dist) and args.config == 2 and not custom and not args.no_other_configs:
+    if (world > 1 or args.force_dist) and full_default:
         # N > 1: the north_star job itself - BASELINE configs[3], 500 000 hap x 10 M sites, its 1221 blocks sharded over
         # these same ranks (strong scaling), with gather_ms, the ranks' times and its own roofline - attached to the
         # weak-scaling line, so that a driver that only runs the default command at N = 1, 2, 4, 8 records it
@@ -619,6 +671,7 @@ def north_star_args(args):
     import copy
     a = copy.copy(args)
     a.config, a.haps, a.sites, a.seed = 3, None, None, None
+    a.dump_outputs = None  # (the outputs dumped are the main line's)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         a.sites_fraction = 1.0  # the whole job; (--force-dist on one GPU: the fraction given, a rehearsal of this path)
     a.steps, a.warmup, a.cpu_sample_cells = 2, 1, 4.2e9
@@ -789,7 +842,7 @@ def run_other_configs(args, t_start):
             res[name] = {"skipped": "wall-time budget of --other-configs-budget-s spent (%.0f s)" % spent}
             continue
         a = copy.copy(args)
-        a.haps = a.sites = a.seed = None
+        a.haps = a.sites = a.seed = a.dump_outputs = None
         a.sites_fraction = 1.0
         for k, v in over.items():
             setattr(a, k, v)
@@ -866,14 +919,17 @@ def run_roundtrip(args, emit=True, dist_sub=False):
     # The step counts the ALT alleles of every row on the device (xsi_hip_encode_packed: the histogram half of
     # GtBlock::scan_genotypes, gt_block.hpp:207-269): the synthetic producer makes no counts.  --producer-counts is the
     # opt-in for a caller whose producer has them (the file writer's packer counts while it packs) and hands them to
-    # xsi_hip_encode_packed_counted; the counting pass alone is timed either way (count_rows_ms).
+    # xsi_hip_encode_packed_counted; with --full the counting pass alone is timed either way (count_rows_ms).
     d_cnt = torch.empty(S, dtype=torch.int32, device=dev)
-    binding.check(L.xsi_hip_count_packed_rows(ctx.handle, d_bits.data_ptr(), S, stride, N, d_cnt.data_ptr()))
-    torch.cuda.synchronize()
-    _t = time.perf_counter()
-    binding.check(L.xsi_hip_count_packed_rows(ctx.handle, d_bits.data_ptr(), S, stride, N, d_cnt.data_ptr()))
-    ctx.synchronize()
-    count_rows_ms = (time.perf_counter() - _t) * 1e3
+    count_rows_ms = None
+    if args.producer_counts or args.full:
+        binding.check(L.xsi_hip_count_packed_rows(ctx.handle, d_bits.data_ptr(), S, stride, N, d_cnt.data_ptr()))
+    if args.full:
+        torch.cuda.synchronize()
+        _t = time.perf_counter()
+        binding.check(L.xsi_hip_count_packed_rows(ctx.handle, d_bits.data_ptr(), S, stride, N, d_cnt.data_ptr()))
+        ctx.synchronize()
+        count_rows_ms = (time.perf_counter() - _t) * 1e3
     count_in_step = not args.producer_counts
     cnt_ptr = None if count_in_step else d_cnt.data_ptr()
     bound = int(L.xsi_hip_encode_bound(ctypes.byref(p), S, S))
@@ -984,8 +1040,19 @@ def run_roundtrip(args, emit=True, dist_sub=False):
         per_rank_ms = [float(e.item()) / steps * 1e3 for e in every]
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the step receives: the blocks region and its offsets from the encode, the packed rows from
+        # the decode (the larger two as samples at fixed positions, the bytes as float32)
+        nb_bytes = int(res.blocks_bytes)
+        pos = torch.from_numpy(sample_positions(nb_bytes, DUMP_VALUES, 1)).to(dev)
+        sel = torch.from_numpy(sample_positions(S, max(1, DUMP_VALUES // stride), 2)).to(dev)
+        dump_outputs(args.dump_outputs, {
+            "xsi_blocks_sample": d_out[pos].float().cpu().numpy(),
+            "block_offsets": d_off.cpu().numpy().astype(np.float64),
+            "decoded_rows_sample": d_dec.view(S, stride)[sel].float().cpu().numpy(),
+            "sizes": np.array([nb_bytes, int(res.n_wah_lines), int(rows.value)], dtype=np.float64)})
     gather_ms = None
-    if distributed:
+    if distributed and args.full:
         # the exchange step alone, not overlapped with anything
         fence()
         tg = time.perf_counter()
@@ -1065,7 +1132,8 @@ def run_roundtrip(args, emit=True, dist_sub=False):
                     kernel_traffic = ent["hbm_bytes_per_launch"]
                     # per STEP, like `achieved`: every kernel's bytes per launch x its launches per step of the profiled run
                     steps_prof = float(tj.get("steps_profiled") or ks.get("k_classify", {}).get("launches_in_the_profiled_run") or 1)
-                    # (outside the steps the command launches the generator and two counting passes: not a step's traffic)
+                    # (outside the steps the profiled command, run with --full, launches the generator and two counting passes:
+                    # not a step's traffic)
                     setup = {"k_synth_packed": None, "k_count_rows_wide": 2, "k_count_rows": 2, "k_count_rows_v4": 2}
                     traffic = sum(v["hbm_bytes_per_launch"] * (v["launches_in_the_profiled_run"] - (setup.get(k) or 0))
                                   for k, v in ks.items() if not (k in setup and setup[k] is None)) / steps_prof
@@ -1116,13 +1184,14 @@ def run_roundtrip(args, emit=True, dist_sub=False):
                          "stage_ms": stages, "stage_ms_per_step": stages_step, "chain_launches_per_step": launches},
             "roundtrip_equal": roundtrip_ok,
         }
-        if not count_in_step:
+        if not count_in_step and count_rows_ms is not None:
             # the same step with the counting pass made on the device as well (measured by itself, outside the timed
             # region, added here): what xsi_hip_encode_packed without producer counts costs
             out["with_device_row_count"] = {"ms_per_step": ms_per_step + count_rows_ms,
                                             "value": cells_job / ((dt / steps) + count_rows_ms * 1e-3)}
-        if gather_ms is not None:
-            out["gather_ms"] = gather_ms
+        if distributed:
+            if gather_ms is not None:
+                out["gather_ms"] = gather_ms
             out["ms_per_step_per_rank"] = per_rank_ms
             region_all, offs_all, per_b, per_n = state["gathered"]  # the last timed step's exchange, on the writer rank
             offs_np = offs_all.cpu().numpy()
@@ -1134,7 +1203,7 @@ def run_roundtrip(args, emit=True, dist_sub=False):
                                else "torch.distributed point-to-point (the library's communicator failed: %s)" % gat_error}
 
     # ---- CPU baseline: the oracle (parity-pinned restatement of the reference), 1 thread ----
-    if rank == 0 and not args.no_cpu_baseline:  # (N > 1: rank 0's host cores, while the other ranks wait at the group's next collective)
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # (N > 1: rank 0's host cores, while the other ranks wait at the group's next collective)
         from oracle import oracle
         full_leg = emit  # a sub-run only encodes its sample with the oracle, for the byte comparison
         cs = int(args.cpu_sample_cells / N)
