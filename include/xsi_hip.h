@@ -253,6 +253,48 @@ int xsi_hip_decode_dot_gt(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_le
                           uint64_t n_blocks, const uint32_t* h_n_allele, uint64_t n_lines, const double* d_pheno,
                           uint32_t n_pheno, double* d_out, uint64_t capacity_lines, uint64_t* h_n_bin);
 
+/*
+ * Weighted genotype scores on the decoded blocks: the transpose of xsi_hip_decode_dot (X^T.W against X.Y), what
+ * polygenic scores (PLINK --score, many score sets at once) and iterative solvers (randomized PCA, ridge / LMM,
+ * conjugate gradients) need next to it.
+ *   Weights: d_weights[r * n_scores + k] = weight of score k for binary line r, binary lines counted from first_block
+ *     in file order (ALT 1 .. n_allele-1 of each BCF line: the row indexing of decode_dot's d_out).  n_weight_lines
+ *     must equal the blocks' binary-line count, or XSI_ERR_ARG.
+ *   Output:  d_out[i * n_scores + k] = sum over binary lines r where dosage(i, r) != 0 of dosage(i, r) * w[r][k];
+ *     i = sample (out_rows >= N_SAMPLES), or haplotype with XSI_SCORE_PER_HAPLOTYPE (out_rows >= N_HAPS); fewer
+ *     rows: XSI_ERR_CAPACITY.  Per sample the dosage is the number of copies of that ALT allele (0..2 on a diploid
+ *     line, 0 / 1 on a fully haploid line); per haplotype it is 0 / 1, and on a fully haploid line sample s is
+ *     credited to haplotype 2s.  Missing and end-of-vector values carry no allele (as decode_dot_gt).
+ *   A weight touches only the carriers of its line: a NaN or inf weight on line r makes only the rows that carry r
+ *     non-finite.
+ *   Determinism: for a given n_scores, out = (XSI_SCORE_ACCUMULATE ? d_out : 0), then out += S_b for every block b in
+ *     order, S_b the block's partial sums, reduced in an order that depends only on that block.  So the bits are the
+ *     same across runs, across any workspace budget (blocks are walked in ranges that fit it), across any split of a
+ *     block range into several calls with XSI_SCORE_ACCUMULATE, and between the two entry points on blocks both take.
+ *   n_scores == 0, a null pointer or unknown flag bits: XSI_ERR_ARG.  zstd images: XSI_ERR_UNSUPPORTED.
+ *   n_scores >= 8 runs on the float64 matrix cores (v_mfma_f64_16x16x4_f64), fewer on the vector units; both take
+ *   fully haploid lines.  Stage "score" of the context's timing covers the contraction and the fold.
+ *
+ * xsi_hip_decode_score: on the ALT-carrier bit planes, like decode_dot: blocks with multi-allelic lines or missing /
+ * end-of-vector entries return XSI_ERR_UNSUPPORTED (use xsi_hip_decode_score_gt); fully haploid lines are covered.
+ */
+#define XSI_SCORE_ACCUMULATE 1u    /* d_out += this call's sums instead of d_out = ... */
+#define XSI_SCORE_PER_HAPLOTYPE 2u /* one output row per haplotype (N_HAPS rows) instead of per sample */
+int xsi_hip_decode_score(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_len, uint64_t first_block,
+                         uint64_t n_blocks, const double* d_weights, uint64_t n_weight_lines, uint32_t n_scores,
+                         double* d_out, uint64_t out_rows, uint32_t flags);
+/*
+ * xsi_hip_decode_score_gt: any block - multi-allelic lines (negated sparse lines with a majority ALT allele included),
+ * missing and end-of-vector values, mixed ploidy, non-default phase.  The genotypes are composed in HBM as for
+ * decode_dot_gt and turned into carrier planes of the plane path's layout, which the same contraction then reads.
+ * h_n_allele[n_lines] as for decode_dot_gt; n_lines not matching the blocks, or sum(n_allele - 1) not matching a
+ * block's binary lines: XSI_ERR_ARG.
+ */
+int xsi_hip_decode_score_gt(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_len, uint64_t first_block,
+                            uint64_t n_blocks, const uint32_t* h_n_allele, uint64_t n_lines,
+                            const double* d_weights, uint64_t n_weight_lines, uint32_t n_scores,
+                            double* d_out, uint64_t out_rows, uint32_t flags);
+
 /* Deterministic synthetic haplotype matrix: writes n_lines packed rows starting
  * at site index first_line.  Generator defined in DESIGN.md; mirrored in numpy for the tests. */
 int xsi_hip_synth_packed(xsi_hip_ctx* ctx, uint64_t seed, uint64_t first_line, uint64_t n_lines, uint32_t n_haps,

@@ -13,6 +13,10 @@ XSI_ERR_FORMAT = -4
 XSI_ERR_UNSUPPORTED = -5
 XSI_ERR_IO = -6
 
+# flags of xsi_hip_decode_score[_gt]
+SCORE_ACCUMULATE = 1
+SCORE_PER_HAPLOTYPE = 2
+
 
 class XsiError(RuntimeError):
     def __init__(self, code, msg):
@@ -59,6 +63,7 @@ SYMBOLS = [
     "xsi_accessor_register_array", "xsi_accessor_unregister_array", "xsi_accessor_alloc_array", "xsi_accessor_free_array", "xsi_hip_gather_block_streams_round",
     "xsi_compress_bcf", "xsi_decompress_bcf", "xsi_hip_ctx_reencode_ranges",
     "xsi_accessor_get_genotypes_batch", "xsi_accessor_prefix_stats",
+    "xsi_hip_decode_score", "xsi_hip_decode_score_gt",
 ]
 
 
@@ -238,6 +243,10 @@ def lib():
     L.xsi_hip_decode_dot.argtypes = [vp, vp, u64, u64, u64, vp, u32, vp, u64, c.POINTER(u64)]
     L.xsi_hip_decode_dot_gt.restype = c.c_int
     L.xsi_hip_decode_dot_gt.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, u32, vp, u64, c.POINTER(u64)]
+    L.xsi_hip_decode_score.restype = c.c_int
+    L.xsi_hip_decode_score.argtypes = [vp, vp, u64, u64, u64, vp, u64, u32, vp, u64, u32]
+    L.xsi_hip_decode_score_gt.restype = c.c_int
+    L.xsi_hip_decode_score_gt.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, u64, u32, vp, u64, u32]
     L.xsi_file_num_samples.restype = c.c_int64
     L.xsi_file_num_samples.argtypes = [c.c_char_p]
     L.xsi_accessor_close.restype = None

@@ -179,7 +179,7 @@ const char* xsi_hip_chain_kernel(uint32_t n_haps, uint64_t n_blocks, int decode)
 const char* xsi_hip_stage_name(int i) {
     static const char* names[XSI_STAGE_COUNT] = {"count_rows", "classify_scan", "chain_encode", "wah_size", "block_layout",
                                                  "write_blocks", "dec_parse_flags", "dec_wah_boundaries", "dec_wah_expand",
-                                                 "chain_decode", "dec_sparse", "gt_unpack", "gt_compose"};
+                                                 "chain_decode", "dec_sparse", "gt_unpack", "gt_compose", "score"};
     return (i >= 0 && i < XSI_STAGE_COUNT) ? names[i] : "";
 }
 

@@ -24,6 +24,7 @@ enum {
     XSI_ST_DEC_SPARSE,     // sparse walk + fill
     XSI_ST_GT_UNPACK,      // int32 rows -> planes (+ side sizing)
     XSI_ST_GT_COMPOSE,     // planes -> int32 rows (+ side planes)
+    XSI_ST_SCORE,          // weighted scores: per-block contraction + fold (xsi_score.hip)
     XSI_STAGE_COUNT
 };
 
