@@ -295,6 +295,38 @@ int xsi_hip_decode_score_gt(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_
                             const double* d_weights, uint64_t n_weight_lines, uint32_t n_scores,
                             double* d_out, uint64_t out_rows, uint32_t flags);
 
+/*
+ * Windowed haplotype linkage disequilibrium on the decoded blocks: the banded part of X.X^T, X the binary-line x
+ * haplotype ALT-carrier matrix (LD pruning, clumping, LD-score regression, fine-mapping).
+ *   Rows: the binary lines of blocks [first_block, first_block + n_blocks) in file order, row r the r-th of them (the
+ *     row indexing of decode_dot's d_out).  Columns: entry j (0 <= j < window) of row r is the pair (r, r + 1 + j).
+ *     The partner may lie in a later block of the file, outside the requested range: the call then also decodes the
+ *     blocks after the range that it needs (at most enough to hold `window` lines, never past the file's last block),
+ *     so splitting a block range into several calls gives exactly the rows of one call over the whole range.
+ *   d_n11[r * window + j] = haplotypes (natural order, N = N_HAPS) that carry the ALT allele on both lines.  A negated
+ *     sparse line counts by its ALT carriers; on a fully haploid line sample s counts as haplotype 2s (the rule of
+ *     XSI_SCORE_PER_HAPLOTYPE), haplotype 2s + 1 carries nothing.
+ *   d_r2[r * window + j] = r^2 as float32 from the exact integers, n_i and n_j the two lines' ALT counts (by the same
+ *     rules), in exactly this order, each step one correctly rounded operation:
+ *       num = (double)((int64)N * n11 - (int64)n_i * n_j)
+ *       den = (double)((int64)n_i * (N - n_i)) * (double)((int64)n_j * (N - n_j))
+ *       r2  = (float)(num * num / den)        NaN where den == 0 (a monomorphic line)
+ *   Sentinel: a pair whose partner lies past the file's last binary line gets 0xFFFFFFFF in d_n11 and NaN in d_r2.
+ *   Either output may be NULL, not both; each given one holds capacity_lines * window elements, capacity_lines below
+ *   the requested blocks' binary-line count: XSI_ERR_CAPACITY.  *h_n_bin (optional) receives the row count.
+ *   XSI_ERR_ARG, before the context is touched: null ctx or file, both outputs null, window 0 or above
+ *   XSI_LD_MAX_WINDOW.  XSI_ERR_UNSUPPORTED: a zstd image, or a requested or look-ahead block with multi-allelic
+ *   lines or missing / end-of-vector entries (the planes alone cover bi-allelic, fully called lines, as for
+ *   decode_dot); fully haploid lines are covered.
+ *   All counts are integers, so the output is the same bits for any workspace budget (blocks are walked in ranges
+ *   that fit it, each with its look-ahead lines decoded again).  Stage "ld" of the context's timing covers the plane
+ *   pre-pass and the pair kernel.
+ */
+#define XSI_LD_MAX_WINDOW 65536u
+int xsi_hip_decode_ld(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_len, uint64_t first_block,
+                      uint64_t n_blocks, uint32_t window, uint32_t* d_n11, float* d_r2,
+                      uint64_t capacity_lines, uint64_t* h_n_bin);
+
 /* Deterministic synthetic haplotype matrix: writes n_lines packed rows starting
  * at site index first_line.  Generator defined in DESIGN.md; mirrored in numpy for the tests. */
 int xsi_hip_synth_packed(xsi_hip_ctx* ctx, uint64_t seed, uint64_t first_line, uint64_t n_lines, uint32_t n_haps,

@@ -179,7 +179,7 @@ const char* xsi_hip_chain_kernel(uint32_t n_haps, uint64_t n_blocks, int decode)
 const char* xsi_hip_stage_name(int i) {
     static const char* names[XSI_STAGE_COUNT] = {"count_rows", "classify_scan", "chain_encode", "wah_size", "block_layout",
                                                  "write_blocks", "dec_parse_flags", "dec_wah_boundaries", "dec_wah_expand",
-                                                 "chain_decode", "dec_sparse", "gt_unpack", "gt_compose", "score"};
+                                                 "chain_decode", "dec_sparse", "gt_unpack", "gt_compose", "score", "ld"};
     return (i >= 0 && i < XSI_STAGE_COUNT) ? names[i] : "";
 }
 
@@ -884,6 +884,7 @@ int decode_prepare(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_len, uint
     P->n_blocks = n_blocks;
     P->version = version;
     P->hap_samples = hap_samples;
+    P->file_blocks = total_blocks;
     DecLines& L = P->L;
     memset(&L, 0, sizeof(L));
     L.N = (uint32_t)N64;

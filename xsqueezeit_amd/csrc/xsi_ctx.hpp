@@ -25,6 +25,7 @@ enum {
     XSI_ST_GT_UNPACK,      // int32 rows -> planes (+ side sizing)
     XSI_ST_GT_COMPOSE,     // planes -> int32 rows (+ side planes)
     XSI_ST_SCORE,          // weighted scores: per-block contraction + fold (xsi_score.hip)
+    XSI_ST_LD,             // windowed LD: plane pre-pass + banded pair counts / r2 (xsi_ld.hip)
     XSI_STAGE_COUNT
 };
 
@@ -104,6 +105,7 @@ struct DecodePlan {
     uint32_t n_blocks = 0, version = 0;
     uint32_t n_bin = 0, n_bcf = 0, n_wah = 0, n_sparse = 0;
     uint64_t hap_samples = 0;
+    uint64_t file_blocks = 0;         // blocks of the whole file (its index), not only of the plan
     bool has_side = false;
     DecBlock* d_blocks = nullptr;
     uint32_t* d_totals = nullptr;
@@ -170,6 +172,9 @@ bool pack_bit_row(const int32_t* gt, uint32_t n, int dp, uint8_t* out);
 // from bit row l where d_fast[l] != 0; second values carry default_phased
 int expand_bit_rows(xsi_hip_ctx* ctx, const uint8_t* d_bits, uint32_t bit_stride, const uint8_t* d_fast, int32_t* d_rows,
                     uint64_t N, uint64_t n_lines, int32_t default_phased);
+// Ranges of whole blocks of P whose bytes (per BCF line, per binary line, per block) fit `budget`, at least one block each:
+// cut points, first 0, last P.n_blocks (xsi_score.hip)
+std::vector<uint32_t> score_ranges(const DecodePlan& P, uint64_t budget, uint64_t per_bcf, uint64_t per_bin, uint64_t per_block);
 // bytes of per-line workspace budget in force for a call made now
 uint64_t ws_budget_now(const xsi_hip_ctx* ctx, const char* prefix = nullptr);
 int encode_side_write(xsi_hip_ctx* ctx, const EncBlock* d_blocks, uint32_t n_blocks, const EncLines& L,

@@ -329,7 +329,7 @@ static int score_args(xsi_hip_ctx* ctx, const void* d_file, const double* d_w, u
 }
 
 // Ranges of whole blocks whose bytes (per BCF line, per binary line, per block) fit `budget`; at least one block each.
-static std::vector<uint32_t> score_ranges(const DecodePlan& P, uint64_t budget, uint64_t per_bcf, uint64_t per_bin, uint64_t per_block) {
+std::vector<uint32_t> score_ranges(const DecodePlan& P, uint64_t budget, uint64_t per_bcf, uint64_t per_bin, uint64_t per_block) {
     std::vector<uint32_t> cuts{0};
     uint64_t used = 0;
     for (uint32_t b = 0; b < P.n_blocks; ++b) {
