@@ -326,6 +326,36 @@ int xsi_hip_decode_score_gt(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_
 int xsi_hip_decode_ld(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_len, uint64_t first_block,
                       uint64_t n_blocks, uint32_t window, uint32_t* d_n11, float* d_r2,
                       uint64_t capacity_lines, uint64_t* h_n_bin);
+/*
+ * xsi_hip_decode_ld_gt: the same band for ANY block - multi-allelic lines (negated sparse lines with a majority ALT
+ * allele included), missing and end-of-vector values, mixed ploidy, non-default phase.  The genotypes are composed in
+ * HBM as for decode_dot_gt and never leave the device.
+ *   Rows and columns as for decode_ld: binary lines in file order (ALT 1 .. n_allele-1 of each BCF line, the row
+ *     indexing of decode_dot_gt), look-ahead blocks by the same rule, the same sentinels (0xFFFFFFFF in d_n11 and
+ *     d_n_called, NaN in d_r2).
+ *   h_n_allele[n_lines]: allele numbers from the first BCF line of first_block on.  n_lines must cover the BCF lines of
+ *     the requested blocks and of every look-ahead block the call reads, and must not exceed the lines left in the
+ *     file; on every block read sum(n_allele - 1) must equal its binary lines; otherwise XSI_ERR_ARG.  A caller holding
+ *     the whole file's allele numbers passes h_all + first_block * block_len, n_lines = total_lines - first_block * block_len.
+ *   Per binary line (BCF line l, ALT k) over the N = N_HAPS haplotypes: X = carriers (the value's allele is k), C = called
+ *     (the value is neither missing nor end-of-vector; another ALT allele of the record is called and does not carry
+ *     the line).  On a fully haploid line sample s is haplotype 2s; haplotype 2s + 1 carries nothing and has the call
+ *     status of 2s.  Per pair, over the haplotypes called on both lines (pairwise complete):
+ *       d_n_called = |C_i & C_j|,  d_n11 = |X_i & X_j|,  a = |X_i & C_j|,  b = |C_i & X_j|
+ *     and d_r2 is decode_ld's formula, in the same order and rounding, with N -> n_called, n_i -> a, n_j -> b: NaN where
+ *     den == 0, n_called == 0 included.
+ *   On blocks decode_ld takes, d_n11 and d_r2 are the same bits as decode_ld's and d_n_called == N.
+ *   Any of the three outputs may be NULL, not all; each given one holds capacity_lines * window elements, capacity_lines
+ *   below the row count: XSI_ERR_CAPACITY.  *h_n_bin (optional) receives the row count.
+ *   XSI_ERR_ARG, before the context is touched: null ctx, file or h_n_allele, all outputs null, window 0 or above
+ *   XSI_LD_MAX_WINDOW.  zstd images: XSI_ERR_UNSUPPORTED.
+ *   Every value is an integer or a function of integers: the same bits for any workspace budget and any split of the
+ *   block range.  Stage "gt_unpack" covers the rows -> carrier / called plane pass, stage "ld" the pair kernels.
+ */
+int xsi_hip_decode_ld_gt(xsi_hip_ctx* ctx, const void* d_file, uint64_t file_len, uint64_t first_block,
+                         uint64_t n_blocks, const uint32_t* h_n_allele, uint64_t n_lines, uint32_t window,
+                         uint32_t* d_n11, float* d_r2, uint32_t* d_n_called, uint64_t capacity_lines,
+                         uint64_t* h_n_bin);
 
 /* Deterministic synthetic haplotype matrix: writes n_lines packed rows starting
  * at site index first_line.  Generator defined in DESIGN.md; mirrored in numpy for the tests. */

@@ -66,7 +66,7 @@ SYMBOLS = [
     "xsi_accessor_register_array", "xsi_accessor_unregister_array", "xsi_accessor_alloc_array", "xsi_accessor_free_array", "xsi_hip_gather_block_streams_round",
     "xsi_compress_bcf", "xsi_decompress_bcf", "xsi_hip_ctx_reencode_ranges",
     "xsi_accessor_get_genotypes_batch", "xsi_accessor_prefix_stats",
-    "xsi_hip_decode_score", "xsi_hip_decode_score_gt", "xsi_hip_decode_ld",
+    "xsi_hip_decode_score", "xsi_hip_decode_score_gt", "xsi_hip_decode_ld", "xsi_hip_decode_ld_gt",
 ]
 
 
@@ -252,6 +252,8 @@ def lib():
     L.xsi_hip_decode_score_gt.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, u64, u32, vp, u64, u32]
     L.xsi_hip_decode_ld.restype = c.c_int
     L.xsi_hip_decode_ld.argtypes = [vp, vp, u64, u64, u64, u32, vp, vp, u64, c.POINTER(u64)]
+    L.xsi_hip_decode_ld_gt.restype = c.c_int
+    L.xsi_hip_decode_ld_gt.argtypes = [vp, vp, u64, u64, u64, vp, u64, u32, vp, vp, vp, u64, c.POINTER(u64)]
     L.xsi_file_num_samples.restype = c.c_int64
     L.xsi_file_num_samples.argtypes = [c.c_char_p]
     L.xsi_accessor_close.restype = None
